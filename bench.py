@@ -32,6 +32,10 @@ Extra objects on the line ("Measurement"):
                  flops a pair (N=1 only)
   cpu_baseline   the PyTorch-CPU port of the reference fallback (oracle/torch_ref.py) on the
                  host cores, bounded sample (rank 0, N=1 only)
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (rank 0) as DIR/<name>.npy:
+flow_2d / flow_3d of the forward, the metrics of the evaluation, flow_3d / corr_2d of the hot path.  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import time
 
@@ -101,7 +105,39 @@ def parse():
                    help="process-group backend; nccl is RCCL.  A single rank joins a world-size-1 nccl group as well, so the one "
                         "collective of the evaluation and the timing protocol's barrier / MAX run on RCCL in every run; 'none' "
                         "(single rank only) skips the group")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its "
+                   "last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def snapshot(outputs):
+    """Device-side copies of a step's returned tensors, taken before later work overwrites the graphs' static outputs."""
+    return {k: v.detach().clone() for k, v in outputs.items()}
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every array: float64 stays float64, everything else is written as float32.  Above DUMP_LIMIT_BYTES
+    in all, an array over its equal share of the limit is written as a fixed sample of its flattened elements: that many
+    distinct indices drawn by a generator seeded with 0, in ascending order, so two runs sample the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(host)) // max(1, len(host))  # (4096: room for each file's .npy header)
+    over = sum(a.nbytes for a in host.values()) > DUMP_LIMIT_BYTES - 4096 * len(host)
+    for name, a in sorted(host.items()):
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 NOMINAL_SCLK_MHZ = 2400.0   # MI355X_MICROARCH.md: peak engine clock
@@ -371,7 +407,7 @@ def eval_leg(model, forward, dev, cfg, batch_size, n_batches, rank, world, dist,
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         dts = [float(x) for x in t.tolist()]
     dt = max(dts)
-    return dt, {
+    return dt, metrics, {
         "frame_pairs_per_s": round(n / dt, 3), "ms_per_batch": round(dt / n_batches * 1e3, 3), "batches_per_rank": n_batches,
         "world_size": dist.get_world_size() if dist is not None else 1,
         "per_rank_frame_pairs_per_s": [round(len(E.shard_indices(n, r, world)) / d, 3) for r, d in enumerate(dts)],
@@ -478,6 +514,8 @@ def main():
             dist.barrier()
         sync()
 
+    last = {}
+
     def timed(step):
         marks = [] if (on_gpu and os.environ.get("RPE_BENCH_STEP_TIMES")) else None  # diagnostic: per-step device times to stderr
         # The host runs one or two replays ahead of the device (a graph launch blocks beyond that), so a host pause longer than a
@@ -498,8 +536,9 @@ def main():
                 if marks is not None:
                     marks.append(torch.cuda.Event(enable_timing=True))
                     marks[-1].record()
-                step()
+                ret = step()
                 host.append(time.perf_counter())
+            last["ret"] = ret  # what the last timed step returned (--dump-outputs)
             if marks is not None:
                 marks.append(torch.cuda.Event(enable_timing=True))
                 marks[-1].record()
@@ -529,10 +568,12 @@ def main():
             dist.destroy_process_group()
 
     if not on_gpu:  # launcher + timing protocol only
-        a = torch.randn(64, 64)
+        a = torch.randn(64, 64, generator=torch.Generator().manual_seed(0))
         for _ in range(args.warmup):
             a @ a
         dt = timed(lambda: a @ a)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"product": last["ret"]})
         return finish({"metric": "selftest steps/s (launcher and timing protocol only, CPU tensors)", "value": round(args.steps * world / dt, 3),
                        "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
@@ -551,6 +592,7 @@ def main():
     # 218 frame-pairs/s, 4 of 8 runs; never in 30 captures without them) -- whatever the runtime derives its queue
     # mapping from depends on what was captured before.
     epe_delta, dt, launch, step_clock = None, None, None, None
+    dumped = None  # --dump-outputs: what the timed path returned in its last step
     eval_info = None
     startup = {"imports_s": round(T_IMPORTED - T_PROCESS, 2)}  # this rank's way to its first step, seconds since its process started
     if args.workload in ("forward", "eval"):
@@ -625,12 +667,17 @@ def main():
             step_clock = runtime.ShaderClock(dev)
             with step_clock:  # one stamp launch in front of and one behind the barriers that bracket the K steps: outside the timed region
                 dt = timed(fwd_step)
+            if args.dump_outputs:  # a graph replay returns nothing: its outputs are the graph's static tensors, which the eval leg reuses
+                dumped = snapshot(out if forward is not None else last["ret"])
         n_eval = args.steps if args.workload == "eval" else args.eval_batches
         if forward is not None and n_eval > 0:
-            dt_eval, eval_info = eval_leg(model, forward, dev, cfg, args.batch, n_eval, rank, world, dist, workers=args.eval_workers,
+            dt_eval, eval_metrics, eval_info = eval_leg(model, forward, dev, cfg, args.batch, n_eval, rank, world, dist, workers=args.eval_workers,
                                           pinned=not args.eval_pageable, backend=args.backend, distinct=args.eval_distinct, raw_events=args.eval_raw_events)
             if args.workload == "eval":
                 dt = dt_eval
+                if args.dump_outputs:
+                    dumped = {k: v for k, v in eval_metrics.items() if k != "counts"}
+                    dumped.update(("count_" + k, float(v)) for k, v in eval_metrics["counts"].items())
             else:
                 eval_info["vs_forward"] = round(eval_info["frame_pairs_per_s"] / (args.batch * args.steps * world / dt), 4)
         elif args.workload == "eval":
@@ -654,6 +701,8 @@ def main():
     dt_hot = timed(hot_step)
     if args.workload == "hotpath":
         dt = dt_hot
+        if args.dump_outputs:
+            dumped = snapshot(dict(zip(("flow_3d", "corr_2d"), last["ret"])))
 
     totals = timer.totals_ms()
     line = None
@@ -750,6 +799,8 @@ def main():
             line["roofline_knn"] = knn_microbench(dev)
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, args.config)
+    if rank == 0 and dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     if rank == 0:
         emit(line)
     if dist is not None:

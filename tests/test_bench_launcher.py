@@ -25,6 +25,39 @@ def test_gpus_2_starts_two_ranks_and_prints_one_line():
     assert line["value"] > 0 and line["ms_per_step"] > 0
 
 
+def test_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: what the timed step returned, as DIR/<name>.npy, the same from run to run (seeded inputs)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        r = run("--workload", "selftest", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        dumps.append(np.load(d / "product.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (64, 64) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_samples_above_64_mb(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = {"flow": np.arange(10_000_000, dtype=np.float64).reshape(2, 5, 1_000_000), "metric": np.float64(1.5)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 10 ** 6
+    a, b = np.load(tmp_path / "a" / "flow.npy"), np.load(tmp_path / "b" / "flow.npy")
+    assert a.ndim == 1 and 0 < a.size < 10_000_000 and np.array_equal(a, b)  # a fixed sample: the same elements every run
+    assert np.all(np.diff(a) > 0)                                            # distinct elements in ascending index order
+    assert np.load(tmp_path / "a" / "metric.npy").dtype == np.float64
+
+
+def test_steps_sets_the_timed_steps():
+    r = run("--workload", "selftest", "--backend", "gloo", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_launcher_world_size_must_match_gpus():
     """Under an outer launcher (WORLD_SIZE set) --gpus has to agree with it: a 1-rank run must not print n_gpus: 8."""
     r = run("--gpus", "2", "--workload", "selftest", "--backend", "gloo", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

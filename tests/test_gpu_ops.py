@@ -34,13 +34,36 @@ def test_library_is_loaded_from_tree():
     assert _lib.lib().rpe_abi_version() == _lib.ABI_VERSION
 
 
-def test_mfma_4x4x1_layout_probe():
+def experimental_library(tmp_path):
+    """The loaded library if it exports the RPE_EXPERIMENTAL entry points, else a library built for this test: correlation.hip
+    with -DRPE_EXPERIMENTAL, linked with the default build's other objects (the default library keeps exporting only what the
+    header declares outside its RPE_EXPERIMENTAL blocks: tests/test_boundary_cpu.py)."""
+    import ctypes
+    import subprocess
+    from rpeflow_amd import build
+    if hasattr(_lib.lib(), "rpe_probe_mfma4x4"):
+        return _lib.lib()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "rpeflow_amd", "csrc")
+    obj, lib = str(tmp_path / "correlation_experimental.o"), str(tmp_path / "librpeflow_experimental.so")
+    subprocess.run(["/opt/rocm/bin/hipcc", *build.FLAGS, "-DRPE_EXPERIMENTAL", "-I", os.path.join(root, "include"), "-I", src, "-c",
+                    os.path.join(src, "correlation.hip"), "-o", obj], check=True, timeout=600)
+    others = [os.path.join(src, "build", f) for f in os.listdir(os.path.join(src, "build")) if f.endswith(".o") and f != "correlation.o"]
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *others, obj], check=True, timeout=600)
+    handle = ctypes.CDLL(lib)
+    handle.rpe_probe_mfma4x4.argtypes, handle.rpe_probe_mfma4x4.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+    handle.rpe_abi_version.restype = ctypes.c_int
+    assert handle.rpe_abi_version() == _lib.ABI_VERSION
+    return handle
+
+
+def test_mfma_4x4x1_layout_probe(tmp_path):
     """The correlation kernel assumes: A lane 4g+i, B lane 4g+j -> D register i, lane 4g+j.  (A development probe: only a
     library built with -DRPE_EXPERIMENTAL exports it; the correlation goldens test the same assumption end to end.)"""
-    if not hasattr(_lib.lib(), "rpe_probe_mfma4x4"):
-        pytest.skip("default build: rpe_probe_mfma4x4 is an RPE_EXPERIMENTAL entry point")
-    out = torch.zeros(256, device=DEV)
-    _lib.check(_lib.lib().rpe_probe_mfma4x4(out.data_ptr(), None), "probe")
+    lib = experimental_library(tmp_path)
+    out = torch.zeros(256, device=DEV)  # one wave of 64 lanes writes 4 floats each
+    _lib.check(lib.rpe_probe_mfma4x4(out.data_ptr(), _lib.stream_of(out)), "probe")
+    torch.cuda.synchronize()
     d = out.cpu().numpy().reshape(64, 4)
     lane = np.arange(64)
     g, j = lane // 4, lane % 4
