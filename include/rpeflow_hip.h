@@ -38,9 +38,7 @@ extern "C" {
 
 typedef void *rpe_stream_t; /* a hipStream_t; NULL = the legacy default stream */
 
-/* RPE_ABI_VERSION in the lower 16 bits.  The upper 16 are 0 in every library that computes right results; a diagnostic build
- * whose kernels drop work on purpose (energy probes, tools/corr_energy_probes.sh) reports its variant there, and
- * rpeflow_amd/_lib.py refuses to load it unless RPE_ALLOW_DIAGNOSTIC_LIB=1 says the caller expects one. */
+/* Returns RPE_ABI_VERSION: the version of this header the library was built against. */
 int rpe_abi_version(void);
 const char *rpe_error_string(int code);
 

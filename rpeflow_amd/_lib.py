@@ -9,7 +9,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RPE_HIP_LIB") or os.path.join(_HERE, "csrc", "librpeflow_hip.so")  # (RPE_HIP_LIB: diagnostic builds, e.g. tools/corr_energy_probes.sh)
+LIB_PATH = os.environ.get("RPE_HIP_LIB") or os.path.join(_HERE, "csrc", "librpeflow_hip.so")  # (RPE_HIP_LIB: another build of the library, e.g. tools/experiments/build_probe.sh)
 
 _c_f32p = ctypes.c_void_p
 _c_i64 = ctypes.c_int64
@@ -129,11 +129,8 @@ def lib():
         handle.rpe_error_string.argtypes = [_c_int]
         handle.rpe_error_string.restype = ctypes.c_char_p
         version = handle.rpe_abi_version()
-        if version >> 16 and os.environ.get("RPE_ALLOW_DIAGNOSTIC_LIB") != "1":
-            raise RuntimeError(f"{LIB_PATH} is a DIAGNOSTIC build (variant {version >> 16}): its kernels compute wrong results on purpose "
-                               "(tools/corr_energy_probes.sh).  Unset RPE_HIP_LIB, or set RPE_ALLOW_DIAGNOSTIC_LIB=1 for a timing run")
-        if version & 0xffff != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH}: ABI version {version & 0xffff}, this package binds version {ABI_VERSION}")
+        if version != ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH}: ABI version {version}, this package binds version {ABI_VERSION}")
         _lib = handle
     return _lib
 

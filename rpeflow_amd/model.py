@@ -11,7 +11,6 @@ Inference only.  The mutual-information heads (models/mutual_info.py) exist as p
 holders so state dicts match, but are not evaluated: their output is a training loss that
 never reaches the flows (RPEFlow_core.py:33-35, RPEFlow.py:95-99).
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -878,7 +877,6 @@ class RPEFlow(nn.Module):
         self.cfgs = cfgs or things_config()
         self.ids_on_host = ids_on_host
         self.overlap_streams = True
-        self.early_hoist = os.environ.get("RPE_EARLY_HOIST", "1") != "0"  # hoisted stage beside the event pyramid (forward())
         self.keep_levels = False  # also return every pyramid level's up-sampled flows, as decode() hands them over (tests)
         self._streams = {}
         self.pwc_fusion_core = RPEFlow_core(self.cfgs.pwc2d, self.cfgs.pwc3d, self.cfgs.get("attention"), ops=ops)
@@ -998,29 +996,20 @@ class RPEFlow(nn.Module):
             with torch.cuda.stream(side):
                 xyzs1, xyzs2, both = self._pyramid(pc1, pc2, n_samples, fps_order)
                 _stamp("side fps done")
-                if self.early_hoist:
-                    feats_3d_both = core.feature_pyramid_3d(both)
-                    _stamp("side encode3d done")
-                    encoded_3d = torch.cuda.Event()
-                    encoded_3d.record(side)
+                feats_3d_both = core.feature_pyramid_3d(both)
+                _stamp("side encode3d done")
+                encoded_3d = torch.cuda.Event()
+                encoded_3d.record(side)
             feats_2d_both = core.feature_pyramid_2d(image_both)
             _stamp("main image pyramid done")
-            if self.early_hoist:
-                # The hoisted stage of every level reads the image and point pyramids only: it starts here, beside the event
-                # pyramid, instead of behind it (the coarsest level's set was what the first decoder level waited for).
-                main.wait_event(encoded_3d)
-                for t in list(xyzs1) + list(xyzs2) + list(feats_3d_both):
-                    t.record_stream(main)  # allocated on the side stream, consumed on the main one
-                early = core.hoist(xyzs1, xyzs2, feats_2d_both, feats_3d_both, None, camera, pre_stream=pre)
+            # The hoisted stage of every level reads the image and point pyramids only: it starts here, beside the event
+            # pyramid, instead of behind it (the coarsest level's set was what the first decoder level waited for).
+            main.wait_event(encoded_3d)
+            for t in list(xyzs1) + list(xyzs2) + list(feats_3d_both):
+                t.record_stream(main)  # allocated on the side stream, consumed on the main one
+            early = core.hoist(xyzs1, xyzs2, feats_2d_both, feats_3d_both, None, camera, pre_stream=pre)
             efeats_2d = core.encode_event(event_voxel)
             _stamp("main event pyramid done")
-            if not self.early_hoist:
-                with torch.cuda.stream(side):
-                    feats_3d_both = core.feature_pyramid_3d(both)
-                    _stamp("side encode3d done")
-                main.wait_stream(side)
-                for t in list(xyzs1) + list(xyzs2) + list(feats_3d_both):
-                    t.record_stream(main)  # allocated on the side stream, consumed on the main one
         else:
             xyzs1, xyzs2, both = self._pyramid(pc1, pc2, n_samples, fps_order)
             feats_3d_both = core.feature_pyramid_3d(both)

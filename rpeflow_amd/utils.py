@@ -10,7 +10,6 @@ here only so that module trees and state-dict keys match the reference.
 """
 import ctypes
 
-import os
 
 import torch
 import torch.nn as nn
@@ -66,7 +65,7 @@ def _inference_only(*tensors):
 # 17.44 ms, <= 0.6e9 17.60, <= 2.5e9 17.33, <= 1e10 17.32, always 17.21 -- even the level-1 projections (13.5 GFLOP), where the
 # library GEMM alone is faster, gain more from the epilogue / residual pass they no longer need.  The library path stays for
 # anything larger than the model produces.
-_PW_MAX_FLOPS = float(os.environ.get("RPE_POINTWISE_MAX_FLOPS", 1e12))
+_PW_MAX_FLOPS = 1e12
 
 
 def _pw_packed_weight(weight):
@@ -154,20 +153,16 @@ class _rocblas:
     GPU): fp32 rocBLAS kernels are built on v_mfma_f32_16x16x4 and measure 1.0-1.4x faster on the model's shapes, 16x on
     the 510 -> 192 projections over 135 positions (hipBLASLt: 16x16x1 tiles; tools/experiments/blas_pref.py).  Host-side dispatch
     state only: safe under graph capture."""
-    lib = os.environ.get("RPE_POINTWISE_BLAS", "cublas")  # PyTorch's name for rocBLAS; "cublaslt": leave the default
 
     def __enter__(self):
-        self.prev = None
-        if self.lib != "cublaslt":
-            import warnings
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                self.prev = torch.backends.cuda.preferred_blas_library()
-                torch.backends.cuda.preferred_blas_library(self.lib)
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            self.prev = torch.backends.cuda.preferred_blas_library()
+            torch.backends.cuda.preferred_blas_library("cublas")  # PyTorch's name for rocBLAS
 
     def __exit__(self, *exc):
-        if self.prev is not None:
-            torch.backends.cuda.preferred_blas_library(self.prev)
+        torch.backends.cuda.preferred_blas_library(self.prev)
 
 
 def is_pointwise(conv):
@@ -188,11 +183,10 @@ def is_pointwise(conv):
 # their time (10x for the whole forward).  Here such a convolution is im2col (F.unfold) + one rocBLAS strided-batched GEMM:
 # fixed summation order, +10 us on the smallest maps, equal from 36 x 60 on (+0.13 ms per forward in all).
 _IM2COL_MAX_POSITIONS = 36000   # batch x output positions: beyond, MIOpen's implicit GEMMs fill the GPU without splitting K
-_IM2COL_TINY_POSITIONS = int(os.environ.get("RPE_IM2COL_TINY", 2200))  # plain 3x3 convolutions up to 18 x 30, batch 4: sometimes given to the splitting kernels too, and (with the epilogue handed to the next unfold, conv_chain) faster than Winograd + its epilogue pass on maps this small: 15.92 -> 15.83 ms per batch; 8700 (36 x 60): no gain
+_IM2COL_TINY_POSITIONS = 2200  # plain 3x3 convolutions up to 18 x 30, batch 4: sometimes given to the splitting kernels too, and (with the epilogue handed to the next unfold, conv_chain) faster than Winograd + its epilogue pass on maps this small: 15.92 -> 15.83 ms per batch; 8700 (36 x 60): no gain
 _IM2COL_MAX_BYTES = 192 << 20   # size of the unfolded input
 # The unfolded GEMM stays on rocBLAS + one epilogue pass: K = 9 Cin is deep (1152 for the context network), where the 1x1 kernel
 # (no K split, four channel groups in flight) loses: forward 17.2 ms with the library GEMM, 18.3 fused below 1 GFLOP, 18.6 always.
-_IM2COL_FUSED_MAX_FLOPS = float(os.environ.get("RPE_IM2COL_FUSED_MAX_FLOPS", 0))
 
 
 def _out_size(n, k, s, p, d):
@@ -228,8 +222,6 @@ def im2col_conv(x, weight, bias, stride, padding, dilation, epilogue=None, pendi
     else:
         assert pending is None
         cols = torch.nn.functional.unfold(x, (k[2], k[3]), dilation=dilation, padding=padding, stride=stride)
-    if x.is_cuda and 2.0 * cols.numel() * k[0] <= _IM2COL_FUSED_MAX_FLOPS:
-        return pointwise_conv(cols, weight, bias, 1, epilogue=epilogue).reshape(B, k[0], ho, wo)
     wb = weight.reshape(1, k[0], -1).expand(B, -1, -1)
     with _rocblas():
         y = torch.bmm(wb, cols) if bias is None else torch.baddbmm(bias.view(1, -1, 1), wb, cols)
@@ -386,7 +378,7 @@ def conv_chain(blocks, x):
     return x
 
 
-_CHAIN_MAX_POSITIONS = int(os.environ.get("RPE_CHAIN_MAX_POSITIONS", 70000))  # batch x positions: up to 72 x 120 x 8 (beyond: GEMM + epilogue)
+_CHAIN_MAX_POSITIONS = 70000  # batch x positions: up to 72 x 120 x 8 (beyond: GEMM + epilogue)
 
 
 def pointwise_chain(blocks, x):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# diagnostic builds of the library: tools/experiments/build_probe.sh <name> <source.hip> <-DDEFINE[=v]> -> tools/experiments/librpe_probe<name>.so
+# another build of the library: tools/experiments/build_probe.sh <name> <source.hip> <-DDEFINE[=v]> -> tools/experiments/librpe_probe<name>.so
 cd "$(dirname "$0")/../.."
 name=$1; src=$2; def=$3
 mkdir -p /tmp/probe$name
