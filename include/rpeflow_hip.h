@@ -146,7 +146,7 @@ int rpe_correlation2d_forward(const float *in1, const float *in2, int B, int C, 
  * behind CorrelationFunction.backward (wrapper.py:27-37), NCHW throughout:
  *   grad_in1[b][c][p] = 1/C sum_k grad_out[b][k][p]       in2[b][c][p + d_k]
  *   grad_in2[b][c][q] = 1/C sum_k grad_out[b][k][q - d_k] in1[b][c][q - d_k]      d_k = (k/(2md+1) - md, k%(2md+1) - md)
- * grad_out [B,(2md+1)^2,H,W]; either gradient pointer may be NULL to skip it.  md <= 4.                     */
+ * grad_out [B,(2md+1)^2,H,W]; either gradient pointer may be NULL to skip it.  Any md >= 0 (md > 4 on a slower path). */
 int rpe_correlation2d_backward(const float *grad_out, const float *in1, const float *in2, int B, int C, int H, int W,
                                int md, float *grad_in1, float *grad_in2, rpe_stream_t stream);
 

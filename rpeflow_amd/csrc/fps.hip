@@ -410,7 +410,15 @@ int launch_fps_plain(const float *xyz, int64_t sb, int64_t sn, int64_t sd, int B
     const size_t full = small + sizeof(float) * 3 * (size_t)N;
     const bool use_lds = full <= 150 * 1024;
     const size_t shmem = use_lds ? full : small;
-    auto kern = use_lds ? fps_kernel_int<PPT, true> : fps_kernel_int<PPT, false>;
+    // N lies in (PPT / 2, PPT] x kThreads (ppt doubles from bucket to bucket; the first bucket starts at 1): only the forms
+    // that some N of this bucket selects are instantiated -- the whole cloud always fits for PPT <= 8, never for PPT = 32
+    constexpr size_t kSmall = sizeof(float) * 4 * kWaves;
+    constexpr int64_t kMinN = PPT == 2 ? 1 : (int64_t)(PPT / 2) * kThreads + 1, kMaxN = (int64_t)PPT * kThreads;
+    constexpr bool kMayLds = kSmall + sizeof(float) * 3 * kMinN <= 150 * 1024;
+    constexpr bool kMayGlobal = kSmall + sizeof(float) * 3 * kMaxN > 150 * 1024;
+    static_assert(kMayLds || kMayGlobal, "some form must be instantiated");
+    auto kern = fps_kernel_int<PPT, kMayLds>;
+    if constexpr (kMayLds && kMayGlobal) kern = use_lds ? fps_kernel_int<PPT, true> : fps_kernel_int<PPT, false>;
     if (shmem > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         if (e != hipSuccess) return (int)e;

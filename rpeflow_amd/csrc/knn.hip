@@ -1556,8 +1556,12 @@ int launch_knn(const KnnJobs &jobs, int njobs, int max_q, int min_m, int max_m, 
             if (e != hipSuccess) return (int)e;
         }
         hipLaunchKernelGGL((knn_select_kernel<D, QW, true>), grid, block, lds, st, jobs, k, ties, row, wide);
-    } else {
+    } else if constexpr (QW != 2) {
         hipLaunchKernelGGL((knn_select_kernel<D, QW, false>), grid, block, 0, st, jobs, k, ties, 0, 0);
+    } else {
+        // pick_qw gives two queries a wave only to k == 1, which the two branches above always take (k == 1 is either
+        // the lane-minimum kernel or, with ties and some M < 64, the LDS selection): no knn_select_kernel<D, 2, false>
+        return RPE_EUNSUPPORTED;
     }
     return rpe_launch_status();
 }

@@ -49,7 +49,8 @@ def cloud(r, B, N, D):
     return (centres[:, r.integers(0, 8, N)] + r.normal(0, 0.05, (B, N, D))).astype(np.float32)
 
 
-BASES = {"knn": 910000, "fps": 920000, "corr": 930000, "sample": 940000, "interp": 950000, "project": 960000}  # first seed per operator
+BASES = {"knn": 910000, "fps": 920000, "corr": 930000, "sample": 940000, "interp": 950000, "project": 960000,
+         "corr_backward": 1010000}  # first seed per operator
 
 
 def run(case, name):
@@ -116,6 +117,34 @@ def test_fuzz_correlation2d():
         ref = O.correlation2d(a, b, md)
         assert got.shape == ref.shape and np.abs(got - ref).max() <= 5e-6, (B, C, H, W_, md, float(np.abs(got - ref).max()))
     assert run(case, "corr") >= 2
+
+
+def test_fuzz_correlation2d_backward():
+    """Gradients of correlation2d (both inputs, or only one) against float64 autograd of the plain restatement, within
+    8 * 2^-24 * sum|terms| (tests/ref64.py): md 0-7 (md > 4 is the any-md path), C across the 8-channel staging tail,
+    ragged H x W across the 16 x 16 tiles, grad_out dense or the stride-0 ones of out.sum()."""
+    from tests import ref64 as R
+
+    def case(r, seed):
+        B, C = int(r.integers(1, 5)), int(r.choice([1, 2, 7, 8, 9, 16, 33]))
+        H, W_ = int(r.integers(1, 24)), int(r.integers(1, 38))
+        md = int(r.integers(0, 8))
+        need = [(True, True), (True, False), (False, True)][int(r.integers(0, 3))]
+        dense = r.random() < 0.5
+        a64 = torch.from_numpy(I.feature_map(r, B, C, H, W_))
+        b64 = torch.from_numpy(I.feature_map(r, B, C, H, W_))
+        go = torch.from_numpy(r.standard_normal((B, (2 * md + 1) ** 2, H, W_), dtype=np.float32)) if dense else torch.ones(1, 1, 1, 1)
+        a, b = a64.to(DEV).requires_grad_(need[0]), b64.to(DEV).requires_grad_(need[1])
+        out = ops.correlation2d(a, b, md)
+        out.backward(go.to(DEV)) if dense else out.sum().backward()
+        ga, gb, aa, ab = R.corr2d_backward(a64, b64, md, go, need)
+        what = str((B, C, H, W_, md, need, dense))
+        for want, got, ref, ref_abs in ((need[0], a.grad, ga, aa), (need[1], b.grad, gb, ab)):
+            if want:
+                R.assert_bound(got.cpu(), ref, ref_abs, 8, what)
+            else:
+                assert got is None, what
+    assert run(case, "corr_backward") >= 2
 
 
 def test_fuzz_bilinear_sampling():
